@@ -2,7 +2,13 @@
 """Benchmark: Mcell-updates/s of the 2D inviscid Burgers FOM time loop.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--time-steps T]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does only what the headline figure needs: it sets up, warms up,
+times the K steps, writes its outputs (--dump-outputs) and prints the result
+line.  Everything else below -- the residual check, per_gpu_alone and the
+"extra JSON objects" that take runs of their own -- runs only with --full.
 
 Unit of work ("step"): ONE FOM TRAJECTORY = run_fom.main's time loop
 (inviscid_burgers_implicit2D, C/hypernet2D.py:72-131): T = 500 implicit time
@@ -29,12 +35,19 @@ NaN arithmetic.  N > 1: row slabs, rank k owning rows [k*rows, (k+1)*rows) of
 the nx x N*rows grid, the one-way halo streamed GPU-to-GPU during the launch
 (DESIGN.md section 7).  value = nx * N*rows * T * K / (max over ranks of the
 wall time of the K timed trajectories), inputs resident in HBM.
-After the timed region every run checks its own result (residual_check):
+After the timed region every --full run checks its own result (residual_check):
 the last step of a trajectory must solve the reference residual,
 ||R(w_T; w_{T-1})|| / ||R(w_{T-1}; w_{T-1})|| < 1e-13 (C/hypernet2D.py:2512-2570),
 computed slab by slab with the south halo rows sent by the rank below
 (burg_slab_residual + torch.distributed send/recv); the bench exits non-zero
 if it fails.
+
+--dump-outputs DIR: after the timed steps, what the last timed step left for
+its caller goes to DIR/<name>.npy (float64; rank r > 0 appends _rank<r> to the
+names): the resident final state and retained states of the trajectory, on a
+fixed seeded sample of rows when the grid is large (dump_outputs).  The inputs
+are the same from run to run (w0 = 1, fixed mu and dt), so two builds can be
+compared output for output.
 
 Extra JSON objects: roofline (the march kernel: algorithmic 32 B per
 cell-update = read the previous state u, v + write the new state u, v,
@@ -42,13 +55,15 @@ SURVEY.md section 8(d); per-launch device time from HIP events on the
 library's stream; peak 8 TB/s; traffic from the committed rocprofv3 PMC
 passes, profiles/pmc_traffic.json), issue_roofline (the compute waves'
 instruction-issue floor per diagonal from the kernel ISA, tools/isa_count.py,
-against the measured time per diagonal), cpu_baseline (the oracle's CPU
+against the measured time per diagonal) -- both from the timed steps' own
+launches, so in every run -- and, with --full, cpu_baseline (the oracle's CPU
 restatement, rank 0 at N = 1, bounded sample: the march on every host
 thread, and the reference's Newton on one core), config2_1024 (BASELINE
 configs[1]: the 1024^2 9-mu snapshot sweep) and end_to_end (run_fom.main's
 timed region at 1024^2 x 500: march + D2H + .npy file).  Only the cpu_baseline leg
 touches oracle/.  rom_pipeline: secondary numbers of the reference's ROM
-driver at 250^2 (sweep, POD, LSPG; --no-rom skips).
+driver at 250^2 (sweep, POD, LSPG; --no-rom skips).  The --no-* switches
+and --stencil-nx 0 drop single legs of a --full run.
 """
 import argparse
 import json
@@ -111,6 +126,14 @@ def parse():
     ap.add_argument("--isa-file", default=os.path.join(ROOT, "profiles", "r06", "pipe_isa.json"))
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip the end-to-end field (1024^2 x 500 trajectory + .npy file)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the residual check and the secondary "
+                         "legs (per_gpu_alone, config2_1024, single_1024, end_to_end, "
+                         "stencil_roofline, rom_pipeline, cpu_baseline); the --no-* switches "
+                         "drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, "
+                         "a fixed seeded sample of rows on large grids)")
     return ap.parse_args()
 
 
@@ -548,7 +571,7 @@ def main():
 
     from finitedifference_amd._lib import BurgersError
     alone = None
-    if world > 1 and nmu == 1 and not args.no_alone:
+    if args.full and world > 1 and nmu == 1 and not args.no_alone:
         # the same per-GPU shape as ONE rank (no halo) on rank 0's GPU, before
         # the collective run: the weak-scaling reference that separates the
         # halo / ramp cost from the tile shape's own rate
@@ -577,8 +600,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, rank, nmu == 1)
     check = None
-    if not args.no_residual_check:
+    if args.full and not args.no_residual_check:
         check = residual_check(ctx, T, dist if world > 1 else None,
                                None if rehearse or world == 1 else dev, args.snap_every)
     cells = nx * ny  # whole job
@@ -681,16 +706,17 @@ def main():
                                  clock_ghz=clk, clock_src=csrc)
             if iss:
                 out["issue_roofline"] = iss
-        if world == 1 and not args.no_1024:
+        full1 = args.full and world == 1
+        if full1 and not args.no_1024:
             out["config2_1024"] = config2_1024(args.pmc_file, args.isa_file)
             out["single_1024"] = single_1024(args.pmc_file, args.isa_file)
-        if world == 1 and not args.no_e2e:
+        if full1 and not args.no_e2e:
             out["end_to_end"] = end_to_end()
-        if world == 1 and args.stencil_nx > 0:
+        if full1 and args.stencil_nx > 0:
             out["stencil_roofline"] = stencil_roofline(args.stencil_nx, pmc_file=args.pmc_file)
-        if world == 1 and not args.no_rom:
+        if full1 and not args.no_rom:
             out["rom_pipeline"] = rom_pipeline()
-        if world == 1 and not args.no_cpu_baseline:
+        if full1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nx, dt, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -730,6 +756,49 @@ def per_gpu_alone(nx, rows, dt, T, args, dev):
             "what": "the per-GPU shape of this line run as ONE rank (single domain, no halo) on "
                     "rank 0's GPU before the collective run; weak_eff_same_shape = value / "
                     "(n_gpus * this)"}
+
+
+DUMP_ROWS = 1 << 19   # sampled rows of a large state (4 MB per float64 column)
+DUMP_COLS = 6         # retained states written, evenly spaced, the last one included
+DUMP_SEED = 20240611
+
+
+def dump_outputs(ctx, out_dir, rank, trajectory):
+    """--dump-outputs: what the last timed step left for its caller, as
+    float64 .npy files in out_dir (at most (2 + DUMP_COLS) * 8 * DUMP_ROWS
+    bytes = 34 MB):
+      rows.npy         the rows of the 2n-vector written (all of them up to
+                       DUMP_ROWS, else a sorted sample from a fixed seed);
+      final_state.npy  the resident state after the step (download()) at
+                       those rows;
+      snap_states.npy  the trajectory states (time-step numbers) written,
+                       DUMP_COLS of the retained ones (retained(), evenly
+                       spaced from the first to the last);
+      snapshots.npy    (rows, states): those columns of the snapshot matrix
+                       (trajectory_snaps()) at those rows.
+    A sweep step (--sweep N) keeps no snapshot matrix on the host side:
+    only rows and final_state.  Ranks above 0 append _rank<r> to the names."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    m = ctx.m
+    if m <= DUMP_ROWS:
+        rows = np.arange(m)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(m, DUMP_ROWS, replace=False))
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    save("rows", rows)
+    save("final_state", ctx.download()[rows])
+    if not trajectory:
+        return
+    first, count, stride = ctx.retained()
+    cols = np.unique(np.linspace(0, count - 1, min(DUMP_COLS, count)).round().astype(np.int64))
+    snaps = np.empty((len(rows), len(cols)))
+    for k, j in enumerate(cols):  # one column at a time: a 4096^2 state is 268 MB
+        snaps[:, k] = ctx.trajectory_snaps(int(j), 1)[rows, 0]
+    save("snap_states", first + cols * stride)
+    save("snapshots", snaps)
 
 
 RESIDUAL_TOL = 1e-13

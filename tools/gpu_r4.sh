@@ -12,7 +12,7 @@ if [ -n "$PYTEST_K" ]; then
   grep -E "PASSED|FAILED|ERROR|Gcell|passed|failed" $O/pytest_gpu.log | tail -40
 fi
 if [ "$BENCH" = "1" ]; then
-  timeout -k 10 400 python bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   cat $O/bench.json
 fi
 echo ALLOK

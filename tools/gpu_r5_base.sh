@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${TAG:-r5base}
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 echo bench ok
 HEAD="bench.py --steps 10 --warmup 2 --no-1024 --no-rom --no-cpu-baseline --no-e2e --stencil-nx 0 --no-residual-check"
 cd /tmp

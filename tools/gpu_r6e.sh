@@ -8,5 +8,5 @@ TAG=prof_r6 bash tools/prof_r6.sh || exit 1
 echo PROF_OK
 SKIP_SUITE=1 TAG=r6e bash tools/gpu_r6.sh || exit 1
 O=gpurun_out/r6e
-timeout -k 10 300 python bench.py --nx 16384 --rows-per-gpu 2048 --snap-every 10 --steps 3 --warmup 1 --no-1024 --no-rom --no-cpu-baseline --stencil-nx 0 --no-e2e > $O/slab_16384x2048.json 2> $O/slab.err || { tail -20 $O/slab.err; exit 1; }
+timeout -k 10 300 python bench.py --full --nx 16384 --rows-per-gpu 2048 --snap-every 10 --steps 3 --warmup 1 --no-1024 --no-rom --no-cpu-baseline --stencil-nx 0 --no-e2e > $O/slab_16384x2048.json 2> $O/slab.err || { tail -20 $O/slab.err; exit 1; }
 echo SLAB_OK

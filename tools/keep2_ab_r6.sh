@@ -9,7 +9,7 @@ O=gpurun_out/${TAG:-ab_keep}; mkdir -p $O
 KL=$PWD/finitedifference_amd/libburgers_hip_keep2.so
 BURG_LIB=$KL timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -k "wide or 4096 or 8192 or retained or slab_wide or steady_blocks or reserve or trajectory_from_initial or n8_slab" > $O/pytest_keep.log 2>&1 || { tail -30 $O/pytest_keep.log; exit 1; }
 tail -1 $O/pytest_keep.log
-B4="bench.py --steps 5 --warmup 1 --no-1024 --no-rom --no-cpu-baseline --stencil-nx 0 --no-e2e"
+B4="bench.py --full --steps 5 --warmup 1 --no-1024 --no-rom --no-cpu-baseline --stencil-nx 0 --no-e2e"
 for r in 1 2 3; do for v in base keep2; do
   L=$PWD/finitedifference_amd/libburgers_hip.so; [ $v = keep2 ] && L=$KL
   BURG_LIB=$L timeout -k 10 200 python3 $B4 > $O/${v}_r$r.json 2> $O/${v}_r$r.err || { tail -5 $O/${v}_r$r.err; exit 1; }

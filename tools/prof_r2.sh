@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${TAG:-prof}
 mkdir -p $O
 cd $R
-B="bench.py --steps ${STEPS:-3} --warmup 1 --no-1024 --no-rom --no-cpu-baseline --stencil-nx 0 ${EXTRA}"
+B="bench.py --full --steps ${STEPS:-3} --warmup 1 --no-1024 --no-rom --no-cpu-baseline --stencil-nx 0 ${EXTRA}"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $B > $O/bench_stats.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
 timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- python3 $B > /dev/null 2> $O/fetch.err || { tail -5 $O/fetch.err; exit 1; }
 timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- python3 $B > /dev/null 2> $O/write.err || { tail -5 $O/write.err; exit 1; }
