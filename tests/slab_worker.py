@@ -1,11 +1,14 @@
 """One rank of the slab tests in tests/test_gpu_parity.py (not a test module):
-its slab of an NX x NY grid (default N x N), T steps from w0 = 1, on device 0,
-rendezvous over gloo; writes its slab snapshot matrix.
+its slab of an NX x NY grid (default N x N), T steps from w0 = 1 (or the
+row-distinct field of tests/fields.py), on device 0, rendezvous over gloo;
+writes its slab snapshot matrix.
 
     slab_worker.py N T OUTDIR [run|sweep|residual|failstate]
     env: SLAB_NY (rows, default N), SLAB_W (pipe tile width, 0 = plan),
          SLAB_TILES (tiles target per rank), SLAB_SNAP_EVERY (default 1),
-         SLAB_DT (default 0.05); writes slab{rank}.npy, .w (tile width) and
+         SLAB_DT (default 0.05), SLAB_W0 (ones | wavy: fields.wavy_state;
+         default ones), SLAB_MU ("m1,m2", default 5.19,0.026);
+         writes slab{rank}.npy, .w (tile width) and
          .halo (halo ring placement: in, out; 1 host, 2 device)
 """
 import os
@@ -27,6 +30,10 @@ def main():
     tiles = int(os.environ.get("SLAB_TILES", "0"))
     every = int(os.environ.get("SLAB_SNAP_EVERY", "1"))
     dt = float(os.environ.get("SLAB_DT", "0.05"))
+    start = os.environ.get("SLAB_W0", "ones")
+    assert start in ("ones", "wavy"), start
+    mu = tuple(float(x) for x in os.environ.get("SLAB_MU", "5.19,0.026").split(","))
+    assert len(mu) == 2, mu
     import torch.distributed as dist
     from finitedifference_amd.dist import make_slab_context, slab_state
     dist.init_process_group("gloo")
@@ -35,8 +42,12 @@ def main():
                             tiles_target=tiles)
     gx = np.linspace(0, 100, N + 1)
     gy = np.linspace(0, 100.0 * ny / N, ny + 1)
-    ctx.set_problem(gx, gy, dt, (5.19, 0.026), allow_nonsquare=(ny != N))
-    w0 = slab_state(np.ones(2 * N * ny), N, ny, rank, world)
+    ctx.set_problem(gx, gy, dt, mu, allow_nonsquare=(ny != N))
+    if start == "wavy":
+        from fields import wavy_state
+        w0 = slab_state(wavy_state(N, ny), N, ny, rank, world)
+    else:
+        w0 = slab_state(np.ones(2 * N * ny), N, ny, rank, world)
     dist.barrier()
     mode = sys.argv[4] if len(sys.argv) > 4 else "run"
     if mode in ("failstate", "failone"):

@@ -16,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+import fields
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -85,6 +86,33 @@ def test_run_fom_fine750_on_eight_ranks(gpu, tmp_path):
         U = np.asarray(S[:N * N, col]).reshape(N, N)
         for got, want in ((U[N // 2, :], g["fine_u_row"][k]), (U[:, N // 2], g["fine_u_col"][k])):
             assert np.linalg.norm(got - want) / np.linalg.norm(want) <= REF_TOL
+
+
+def test_thinned_cache_8192x256_on_four_ranks_w256(gpu, orc, tmp_path):
+    """configs[3]'s rank count and tile width through the reference API: an
+    8192 x 256 grid on 4 ranks (64-row slabs: every strip a halo strip, the
+    middle ranks read and write a ring), W = 256, 40 steps from the
+    row-distinct field of tests/fields.py, snap_every = 10.  The one cache
+    file (+every10) holds the oracle's sequential march bit for bit -- the
+    oracle, not the single-GPU file, which is code under test too."""
+    c, = fields.CASES["job"]
+    assert (c.nx, c.ny, c.world, c.W, c.T, c.every, c.mu) == (8192, 256, 4, 256, 40, 10,
+                                                              (4.25, 0.015))
+    job = tmp_path / "job"
+    job.mkdir()
+    infos = _run_job(job, c.world, ["slabwide", c.nx, c.ny, c.T, c.every, c.W, *map(repr, c.mu)],
+                     timeout=110)
+    name = "mu1_%r+mu2_%r+every%d.npy" % (c.mu + (c.every,))
+    assert "+every10" in name and sorted(os.listdir(job / "param_snaps")) == [name]
+    ncols = c.T // c.every + 1
+    assert all(i["shape"] == [2 * c.nx * c.ny, ncols] for i in infos), infos
+    assert len({i["digest"] for i in infos}) == 1, infos
+    ref = fields.problem(orc, c).march_traj(fields.wavy_state(c.nx, c.ny), c.T, c.every)
+    assert fields.identical_fraction(ref, c.nx, c.ny, c.world) <= fields.BLIND_CAP
+    S = np.load(job / "param_snaps" / name, mmap_mode="r")
+    assert S.shape == (2 * c.nx * c.ny, ncols) and S.dtype == np.float64
+    diff = fields.first_difference(S, ref, c.nx, c.ny, c.world)
+    assert diff is None, diff
 
 
 def test_thinned_cache_16384x2048_on_two_ranks(gpu, tmp_path):

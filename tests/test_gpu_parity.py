@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import fields
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -445,6 +446,29 @@ def test_pipe_wide_bitwise_sequential_march(gpu, orc, N, ny, W, T):
     assert st["nonfinite_diagonals"] == 0
 
 
+@pytest.mark.parametrize("c", fields.CASES["strip"], ids=fields.case_id)
+def test_pipe_strip_boundaries_distinct_rows(gpu, orc, c):
+    """One process, several 64-row strips, 20 steps (the 16 sentinel colours
+    once round) from the row-distinct field of tests/fields.py: the row a
+    strip hands to the one above differs from its neighbours in every column,
+    so a mailbox that carries the wrong row shows.  Narrow (W = 8, 16) and
+    wide tiles, partial tiles and partial strips.  The
+    2100 x 130 case turns slightly negative at dt = 0.05 > h and stays
+    finite: bits are compared all the same."""
+    P = fields.problem(orc, c)
+    w0 = fields.wavy_state(c.nx, c.ny)
+    ref = P.march_traj(w0, c.T)
+    assert fields.identical_fraction(ref, c.nx, c.ny) <= fields.BLIND_CAP
+    ctx = FOMContext_for(c.nx, c.ny, engine="pipe", stream_w=c.W)
+    ctx.set_problem(P.grid_x, P.grid_y, P.dt, P.mu, allow_nonsquare=(c.nx != c.ny))
+    snaps, st, _, _ = ctx.run(w0, c.T)
+    assert st["engine"] == 2
+    assert st["stream_w"] == c.W
+    assert snaps.shape == (P.m, c.T + 1)
+    diff = fields.first_difference(snaps, ref, c.nx, c.ny)
+    assert diff is None, diff
+
+
 def test_pipe_4096_bitwise(gpu, orc):
     """BASELINE config 3 (4096^2, one GPU) on the engine the planner picks
     (pipe, W = 256: 1024 tiles): 3 steps from w0 = 1, bit-equal to the oracle."""
@@ -603,6 +627,38 @@ def test_slab_wide_tile_steady_blocks_one_gpu(gpu, orc, tmp_path, W, N, T, world
         assert np.array_equal(snaps[:, j], ref[j]), f"step {j}"
 
 
+@pytest.mark.parametrize("c", fields.CASES["slab"], ids=fields.case_id)
+def test_slab_production_widths_distinct_rows(gpu, orc, tmp_path, c):
+    """The slab tilings at their production rank counts and widths (4 ranks
+    at W = 256 on 8192-wide rows, 8 ranks at W = 512 on 16384-wide rows; thin
+    slabs whose only strip is the halo strip on both sides, slabs off the
+    64-row grid, a partial last tile against the ring row of ntj * W), and the
+    older small cases again, all from the row-distinct field of
+    tests/fields.py: the row handed over a strip or rank boundary differs
+    from both neighbours in every column (asserted on the oracle's states
+    first), so a halo off by one row, or wrong in a few tiles only, shows.
+    Every stored state is the oracle's sequential march bit for bit."""
+    import json
+    env = dict(SLAB_NY=c.ny, SLAB_W=c.W, SLAB_DT=repr(c.dt), SLAB_SNAP_EVERY=c.every,
+               SLAB_W0="wavy", SLAB_MU="%r,%r" % c.mu)
+    _run_slabs(tmp_path, c.nx, c.T, c.world, **env)
+    widths = [int(open(os.path.join(tmp_path, f"slab{r}.w")).read()) for r in range(c.world)]
+    assert len(set(widths)) == 1 and (c.W == 0 or widths[0] == c.W), widths
+    assert _halo_modes(tmp_path, c.world) == [(0 if r == 0 else 2, 0 if r == c.world - 1 else 2)
+                                              for r in range(c.world)]
+    stats = [json.load(open(os.path.join(tmp_path, f"slab{r}.stats"))) for r in range(c.world)]
+    print(f"{c.id}: W {widths[0]}, loop_ms per rank", [round(d["loop_ms"], 3) for d in stats])
+    assert [d["bounds_hits"] for d in stats] == [0] * c.world, stats
+    ref = fields.problem(orc, c).march_traj(fields.wavy_state(c.nx, c.ny), c.T, c.every)
+    assert fields.identical_fraction(ref, c.nx, c.ny, c.world) <= fields.BLIND_CAP
+    from finitedifference_amd.dist import assemble_snaps
+    parts = [np.load(os.path.join(tmp_path, f"slab{r}.npy")) for r in range(c.world)]
+    snaps = assemble_snaps(parts, c.nx, c.ny)
+    assert snaps.shape == (ref.shape[1], c.T // c.every + 1)
+    diff = fields.first_difference(snaps, ref, c.nx, c.ny, c.world)
+    assert diff is None, f"{c.id} (stored every {c.every} steps): {diff}"
+
+
 def test_fine750_eight_uneven_slabs_one_gpu(gpu, orc, tmp_path):
     """SURVEY.md 8(d) C5 parity case on one GPU: 750^2 over 8 slab processes
     (uneven 94/93-row slabs), 500 steps with snap_every=100: assembled
@@ -669,6 +725,24 @@ def test_sweep_each_trajectory_bitwise(gpu, orc, monkeypatch, N, ny, W, T, nmu, 
             assert np.array_equal(sn[:, j], ref[j]), f"mu={mu} step {j}"
     # the last trajectory's final state is left resident
     assert np.array_equal(ctx.download(), snaps[-1][:, T])
+
+
+@pytest.mark.parametrize("c", fields.CASES["sweep"], ids=fields.case_id)
+def test_sweep_nonuniform_rows_bitwise(gpu, orc, c):
+    """burg_sweep from the row-distinct field of tests/fields.py (a
+    non-uniform w0: the unpaired sweep kernel), 4 strips: every trajectory is
+    its own mu's oracle march from the same w0, bit for bit."""
+    w0 = fields.wavy_state(c.nx, c.ny)
+    P0 = fields.problem(orc, c, c.mus[0])
+    ctx = FOMContext_for(c.nx, c.ny, engine="pipe", stream_w=c.W)
+    ctx.set_problem(P0.grid_x, P0.grid_y, P0.dt, P0.mu, allow_nonsquare=(c.nx != c.ny))
+    snaps, st = ctx.sweep(c.mus, c.T, w0=w0)
+    assert st["engine"] == 2 and st["stream_w"] == c.W and st["steps"] == len(c.mus) * c.T
+    for mu, sn in zip(c.mus, snaps):
+        ref = fields.problem(orc, c, mu).march_traj(w0, c.T)
+        assert fields.identical_fraction(ref, c.nx, c.ny) <= fields.BLIND_CAP
+        diff = fields.first_difference(sn, ref, c.nx, c.ny)
+        assert diff is None, f"mu={mu}: {diff}"
 
 
 def test_sweep_snap_every_and_resident(gpu, orc):
