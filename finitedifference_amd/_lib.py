@@ -239,8 +239,15 @@ def build_flags():
     return load().burg_build_flags().decode()
 
 
+def flags_are_default(flags):
+    """True for the flag string of the default build only: it ends in
+    'knobs: none' and names no -DBURG_ knob anywhere (one passed through
+    HIPFLAGS instead of KNOBS still makes a knob build)."""
+    return flags.endswith("knobs: none") and "-DBURG_" not in flags
+
+
 def is_default_build():
-    return build_flags().endswith("knobs: none")
+    return flags_are_default(build_flags())
 
 
 def ring_audit(W, num_steps, snap_every=1, ring_cap=0, paired=False, paired_layout=False):

@@ -11,6 +11,15 @@
 #include <cstddef>
 #include <cstdint>
 
+// Build knobs of removed experiments (DESIGN.md sections 4.1h and 8a): a
+// leftover -D must stop the build, not yield a default library whose
+// burg_build_flags() names a variant.
+#if defined(BURG_AB_SKIP) || defined(BURG_AB_NOCHECK) || defined(BURG_KEEP_BLOCK) || \
+    defined(BURG_W512_U8) || defined(BURG_TWO_PER_CU) || defined(BURG_WIDE_U16) || \
+    defined(BURG_WIDE_U16_512) || defined(BURG_SE_OPT) || defined(BURG_PIPE_R)
+#error "removed build knob: BURG_AB_SKIP, BURG_AB_NOCHECK, BURG_KEEP_BLOCK, BURG_W512_U8, BURG_TWO_PER_CU, BURG_WIDE_U16, BURG_WIDE_U16_512, BURG_SE_OPT and BURG_PIPE_R no longer exist (DESIGN.md section 8a)"
+#endif
+
 namespace burg {
 
 constexpr int kWave = 64;  // CDNA wavefront; also the tile height (one lane per row)
@@ -212,13 +221,9 @@ struct StreamArgs {
 // Same tiles and ring as the streaming engine; a workgroup holds 4 adjacent
 // tiles of one strip (4 compute waves) plus one comm wave.  Global mailboxes
 // use two sentinel colours so that a slot's emptiness is tied to a step.
-#ifndef BURG_PIPE_R
-#define BURG_PIPE_R 8
-#endif
-constexpr int kPipeR = BURG_PIPE_R;  // global mailbox slots (steps) per edge, power of two
+constexpr int kPipeR = 8;  // global mailbox slots (steps) per edge, power of two
 // (8 is the only depth run and tested; a 16-step build failed its first wait
-// in round 5, profiles/r05/ab/narrow/r16_error.txt -- refuse other depths)
-static_assert(kPipeR == 8, "BURG_PIPE_R: only 8-step mailboxes are supported");
+// in round 5, profiles/r05/ab/narrow/r16_error.txt)
 constexpr int kPipeRL = 4;  // LDS ring slots (steps) per intra-workgroup edge
 constexpr int kPipeSweepMax = 9;   // trajectories per sweep launch (LDS-resident tables)
 

@@ -118,29 +118,10 @@ constexpr unsigned G = kPipeGranuleStride;
 #ifndef BURG_LOADERS
 #define BURG_LOADERS 2
 #endif
-// BURG_AB_SKIP (A/B ceiling probe, wrong results): diagonals per W of the
-// wide tiles whose previous states the loader does not read back (0: off)
-#ifndef BURG_AB_SKIP
-#define BURG_AB_SKIP 0
-#endif
-// BURG_KEEP_BLOCK (round 6): the
-// wide tiles keep the outputs of ONE block of U diagonals per W -- the block
-// at diagonal kKeepS mod W -- in VGPRs of the compute wave, and read the next
-// step's previous states of that block from there instead of the HBM ring
-// (the loader skips their read-back); 0: every previous state from the ring
-#ifndef BURG_KEEP_BLOCK
-#define BURG_KEEP_BLOCK 0
-#endif
-constexpr int kKeepS = 64;  // (a steady / interior block for every W >= 128)
-// BURG_KEEP_BLOCK=2: only the block's first half (8 diagonals, 32 VGPRs) is
-// kept; the loader reads its other half back as usual
-template <int W>
-constexpr int uw_of();
-template <int W>
-constexpr int keep_n_of() { return BURG_KEEP_BLOCK == 2 ? uw_of<W>() / 2 : uw_of<W>(); }
-template <int W>
-constexpr bool keep_of() { return BURG_KEEP_BLOCK && (W == 128 || W == 256); }  // (W >= 512: the loader's
-                                                                                 // column-table DMAs ride with the window's)
+// (Every previous state of a wide tile comes from the HBM ring: keeping one
+// block of U diagonals per W -- or its first half -- in the compute wave's
+// VGPRs instead was measured 3.1 % / 0.4 % slower at 4096^2, on register
+// pressure: DESIGN.md section 4.1h, profiles/r06/ab/keep_block/.)
 constexpr int kSL = 16;   // comm lanes per compute wave for the south / north streams
 #ifndef BURG_KLA
 #define BURG_KLA 16
@@ -158,39 +139,23 @@ constexpr int kSL = 16;   // comm lanes per compute wave for the south / north s
 #ifndef BURG_NARROW_U
 #define BURG_NARROW_U 8
 #endif
-// steady-edge diagonals, round 4: one lane-compare per diagonal instead of two
-// (atE from the next diagonal's at0) and the narrow tiles' column-0 source +
-// inlet sum once per block (A/B knob: 0 = the round-3 code)
-#ifndef BURG_SE_OPT
-#define BURG_SE_OPT 1
-#endif
-// the comm wave's poll window (diagonals ahead of a compute wave's progress):
-// at least two blocks, so the next block's inflows arrive during this one
-template <int W>
-constexpr int la_of();
-// Wide tiles run one workgroup per CU with a 16-diagonal window and blocks of
-// 8.  Built with -DBURG_TWO_PER_CU=1, W = 64 and 128 run two workgroups per CU
-// instead (two compute waves per SIMD: one wave's scalar, LDS and memory
-// instructions issue beside the other's fp64 VALU -- 1.25x the compute rate
-// per SIMD), which leaves 80 KB of LDS per workgroup: a 12-diagonal window,
-// blocks of 4.  Measured at 4096^2 (W = 128, 2048 tiles) the longer
-// hand-off chains then stall 20-27 % of the time and the whole runs slower
-// (118-124 vs 135 Gcell-updates/s for W = 256), so it is off by default.
-#ifndef BURG_TWO_PER_CU
-#define BURG_TWO_PER_CU 0
-#endif
-// the wide tiles' window of previous states, diagonals per compute wave: a
+// Wide tiles run one workgroup per CU.  Two per CU for W = 64 and 128 (two
+// compute waves per SIMD: one wave's scalar, LDS and memory instructions issue
+// beside the other's fp64 VALU -- 1.25x the compute rate per SIMD) left 80 KB
+// of LDS per workgroup, a 12-diagonal window and blocks of 4: measured at
+// 4096^2 (W = 128, 2048 tiles) the longer hand-off chains then stalled
+// 20-27 % of the time and the whole ran slower (118-124 vs 135
+// Gcell-updates/s for W = 256), so that build was removed.
+//
+// The window of previous states of W = 32, 64, diagonals per compute wave: a
 // multiple of the block -- the loader fills up to KWIN - U diagonals ahead of
-// the block being computed (W = 1024: 16, its column table takes the room; 24
-// for W <= 512 measured no faster than 16)
+// the block being computed (24 measured no faster than 16)
 #ifndef BURG_KWIN
 #define BURG_KWIN 16
 #endif
+// loader waves per wide workgroup
 template <int W>
-constexpr bool two_per_cu() { return BURG_TWO_PER_CU && (W == 64 || W == 128); }
-// loader waves (BURG_LOADERS; at most 2 where two workgroups share a CU)
-template <int W>
-constexpr int nl_of() { return two_per_cu<W>() ? (BURG_LOADERS < 2 ? BURG_LOADERS : 2) : BURG_LOADERS; }
+constexpr int nl_of() { return BURG_LOADERS; }
 // BURG_STORE_WAVE (round 6): the
 // one-cell W = 16 kernels' trajectory-ring stores are issued by a sixth wave
 // that copies each compute wave's finished diagonals from its LDS state
@@ -205,7 +170,7 @@ constexpr bool store_wave_of() { return BURG_STORE_WAVE && W == 16; }
 template <int W>
 constexpr int threads_of()
 {
-    return W > 16 ? (5 + nl_of<W>()) * kWave : (store_wave_of<W>() ? 6 : 5) * kWave;  // + loader / store wave
+    return W > 16 ? (5 + BURG_LOADERS) * kWave : (store_wave_of<W>() ? 6 : 5) * kWave;  // + loaders / store wave
 }
 // Blocks of 16 diagonals for W = 128 ... 1024 (round 3 for 128, 256; window
 // 32 diagonals, LDS rings of 2 steps between the workgroup's waves -- the
@@ -215,38 +180,27 @@ constexpr int threads_of()
 // W = 512, 1024 (round 4): their full column tables (8 / 16 KB per wave)
 // left no room for the 32-diagonal window, so they keep a rolling window of
 // the last kCCW columns instead (ccw_of), refilled by the loader wave.
-#ifndef BURG_WIDE_U16
-#define BURG_WIDE_U16 1
-#endif
-#ifndef BURG_WIDE_U16_512
-#define BURG_WIDE_U16_512 1
-#endif
-// BURG_W512_U8 (A/B build, round 5): W = 512 with blocks of 8 in the same
-// 32-diagonal window (the loader then runs up to 3 blocks ahead instead of
-// 1) and the rolling column table
-#ifndef BURG_W512_U8
-#define BURG_W512_U8 0
-#endif
+// (W = 512 with blocks of 8 in the same window and table, the loader up to 3
+// blocks ahead instead of 1, was measured 15 % slower in round 5:
+// profiles/r05/ab/README.md.)
 template <int W>
-constexpr bool u16_of()
-{
-    return BURG_WIDE_U16 && !two_per_cu<W>() &&
-           (W == 128 || W == 256 || (BURG_WIDE_U16_512 && ((W == 512 && !BURG_W512_U8) || W == 1024)));
-}
-// Rolling column table (W >= 512 with blocks of 16): slot t mod kCCW holds
-// {hx, src} of local time t's column while lanes can need it.  A block at
+constexpr bool u16_of() { return W >= 128; }  // (W: a power of two up to 1024)
+// Rolling column table (W >= 512): slot t mod kCCW holds {hx, src} of local
+// time t's column while lanes can need it.  A block at
 // diagonal sb reads t in [sb - 63, sb + U); the loader writes the columns of
 // the blocks it fills, t in [prog + U, prog + KWIN) (prog = the compute
 // wave's block): 95 < kCCW apart, so no live slot is overwritten.
 constexpr int kCCW = 128;
 template <int W>
-constexpr bool ccw_of() { return (u16_of<W>() || (BURG_W512_U8 && W == 512)) && W >= 512; }
+constexpr bool ccw_of() { return W >= 512; }
 template <int W>
 constexpr int ccn_of() { return ccw_of<W>() ? kCCW : W; }  // column-table slots (before padding)
 template <int W>
-constexpr int win_of() { return two_per_cu<W>() ? 12 : (u16_of<W>() || (BURG_W512_U8 && W == 512)) ? 32 : W >= 1024 ? 16 : BURG_KWIN; }  // window (diagonals)
+constexpr int win_of() { return u16_of<W>() ? 32 : BURG_KWIN; }  // window (diagonals)
 template <int W>
-constexpr int uw_of() { return two_per_cu<W>() ? 4 : u16_of<W>() ? 16 : 8; }  // block (diagonals)
+constexpr int uw_of() { return u16_of<W>() ? 16 : 8; }  // block (diagonals)
+// the comm wave's poll window (diagonals ahead of a compute wave's progress):
+// at least two blocks, so the next block's inflows arrive during this one
 // (blocks of 16: 32 diagonals; BURG_U16_LA for A/B builds)
 #ifndef BURG_U16_LA
 #define BURG_U16_LA 32
@@ -529,7 +483,6 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
     // the probe verified (tools/probes/dma_high_probe.hip: 0 .. 160 KB)
     static_assert(offsetof(Img, win) == 0 && sizeof(Img::win) <= 160 * 1024,
                   "LDS-DMA window outside the probed range");
-    static_assert(!(u16_of<W>() && two_per_cu<W>()), "blocks of 16 need the whole CU's LDS");
     constexpr bool WIDE = is_wide<W>();
     // three narrow W=8 workgroups per CU: room for 8 slab processes sharing one
     // GPU (the 750^2 C5 case, tests/test_gpu_parity.py) with all grids resident
@@ -838,40 +791,20 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
         for (;;) {
             bool left = false;
             int got[4] = {0, 0, 0, 0};  // blocks issued this round, per wave
-            int nld[4] = {0, 0, 0, 0};  // their loads
+            // (nld, la: the loads issued after wave k's, counted exactly -- what
+            // is left of the removed kept-block experiment, DESIGN.md section
+            // 4.1h, whose half-block mode waited on la.  Nothing reads la now,
+            // but without these four lines the compiler lays the loop out
+            // differently and allocates the six wide kernels' registers anew,
+            // so they go with a change that measures every width:
+            // profiles/r07/ab/keep_remnants/README.md.)
+            int nld[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (k >= nval) continue;
                 if ((k * nl_of<W>()) >> 2 != lw) continue;  // (this loader's compute waves)
                 const int pk = lds_ldi(&sm.prog[k]), dk = lds_ldi(&sm.done[k]);
                 const int lim = min(min(total, pk + KWIN), dk + W);  // multiples of U
-                // (kept half block: only its last U - KN rows are read back)
-                const bool khalf = keep_of<W>() && keep_n_of<W>() < U && nf[k] >= W &&
-                                   (nf[k] & (W - 1)) == kKeepS;
-                if constexpr (keep_of<W>() && keep_n_of<W>() == U) {
-                    // the kept block's previous states are in the compute
-                    // wave's registers (after the first W diagonals): no read
-                    if (nf[k] < lim && nf[k] >= W && (nf[k] & (W - 1)) == kKeepS) {
-                        if (ret) (void)rc[k].next(a, W, U);  // (the walk moves on)
-                        nf[k] += U;
-                        if (lane == 0) lds_sti(&sm.filled[k], nf[k]);  // (earlier blocks: published)
-                        left |= nf[k] < total;
-                        continue;
-                    }
-                }
-#if BURG_AB_SKIP > 0
-                // A/B ceiling probe only (WRONG results):
-                // the blocks of diagonals 64 .. 64 + BURG_AB_SKIP of every W
-                // (after the first W) are not read back from the ring -- the
-                // rate a read-back cut of that share could reach at most
-                if (nf[k] < lim && nf[k] >= W && (unsigned)((nf[k] & (W - 1)) - 64) < (unsigned)BURG_AB_SKIP) {
-                    if (ret) (void)rc[k].next(a, W, U);
-                    nf[k] += U;
-                    if (lane == 0) lds_sti(&sm.filled[k], nf[k]);  // (earlier blocks: published)
-                    left |= nf[k] < total;
-                    continue;
-                }
-#endif
                 if (nf[k] < lim) {
                     const __amdgpu_buffer_rsrc_t ring =
                         rsrc(a.ring + (size_t)(ti * ntj + tj0 + k) * a.Lt * kWave, (size_t)a.Lt * kWave * 16);
@@ -883,19 +816,12 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
                         e = e < 0 ? e + L : e;
                     }
                     int slot = nf[k] % KWIN;
-                    if (khalf) {
-                        // (a block's U entries are consecutive: plain ring
-                        // with a wrap, retained windows without one)
-                        constexpr int KN = keep_n_of<W>() < U ? keep_n_of<W>() : 0;
-                        e = ret ? e + KN : (e + KN >= L ? e + KN - L : e + KN);  // (windows lie past L)
-                        slot += KN;
-                    }
                     if constexpr (ccw_of<W>()) {
                         // the block's U columns into the rolling table (slot
                         // t mod kCCW, and its padding copy for the first U
                         // slots; else the same slot again): 2 DMAs of U lanes,
                         // issued before the window rows, landed by the same
-                        // waits (kLoadsPerBlock per block)
+                        // waits (NB loads per block)
                         const __amdgpu_buffer_rsrc_t colc = rsrc(colc_d + (size_t)(tj0 + k) * W, (size_t)W * 16);
                         const int sl = nf[k] & (kCCW - 1);
                         const unsigned co = (unsigned)((nf[k] + lane) & (W - 1)) * 16u;
@@ -905,26 +831,14 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
                                                                      co, 0, 0, 0);
                         }
                     }
-                    if (khalf) {
-                        constexpr int KN = keep_n_of<W>() < U ? keep_n_of<W>() : 0;
 #pragma unroll
-                        for (int u = KN; u < U; ++u) {
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(ring, (LDS void *)&sm.win[k][slot][0], 16,
-                                                                     (unsigned)e * 1024u + lane * 16u, 0, 0, BURG_LOAD_AUX);
-                            e = e + 1 == L ? 0 : e + 1;
-                            slot = slot + 1 == KWIN ? 0 : slot + 1;
-                        }
-                        nld[k] = U - KN;
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(ring, (LDS void *)&sm.win[k][slot][0], 16,
-                                                                     (unsigned)e * 1024u + lane * 16u, 0, 0, BURG_LOAD_AUX);
-                            e = e + 1 == L ? 0 : e + 1;
-                            slot = slot + 1 == KWIN ? 0 : slot + 1;
-                        }
-                        nld[k] = U + (ccw_of<W>() ? 2 : 0);
+                    for (int u = 0; u < U; ++u) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(ring, (LDS void *)&sm.win[k][slot][0], 16,
+                                                                 (unsigned)e * 1024u + lane * 16u, 0, 0, BURG_LOAD_AUX);
+                        e = e + 1 == L ? 0 : e + 1;
+                        slot = slot + 1 == KWIN ? 0 : slot + 1;
                     }
+                    nld[k] = U + (ccw_of<W>() ? 2 : 0);
                     nf[k] += U;
                     got[k] = 1;
                 }
@@ -936,32 +850,18 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
                 // after it) loads are outstanding
                 constexpr int NB = U + (ccw_of<W>() ? 2 : 0);  // loads per block
                 int after = nb;
-                // (kept half blocks: the loads issued after wave k's, counted
-                // exactly -- multiples of 8 up to 3 x 16)
                 int la = nld[0] + nld[1] + nld[2] + nld[3];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     if (!got[k]) continue;
                     --after;
                     la -= nld[k];
-                    if constexpr (keep_of<W>() && keep_n_of<W>() < U) {
-                        static_assert(NB == 16 && U == 16, "kept half blocks: blocks of 16 rows");
-                        switch (la >> 3) {
-                        case 0: wait_vmcnt<0>(); break;
-                        case 1: wait_vmcnt<8>(); break;
-                        case 2: wait_vmcnt<16>(); break;
-                        case 3: wait_vmcnt<24>(); break;
-                        case 4: wait_vmcnt<32>(); break;
-                        case 5: wait_vmcnt<40>(); break;
-                        default: wait_vmcnt<48>(); break;
-                        }
-                    } else {
-                        switch (after) {
-                        case 0: wait_vmcnt<0>(); break;
-                        case 1: wait_vmcnt<NB>(); break;
-                        case 2: wait_vmcnt<2 * NB>(); break;
-                        default: wait_vmcnt<3 * NB>(); break;
-                        }
+                    (void)la;
+                    switch (after) {
+                    case 0: wait_vmcnt<0>(); break;
+                    case 1: wait_vmcnt<NB>(); break;
+                    case 2: wait_vmcnt<2 * NB>(); break;
+                    default: wait_vmcnt<3 * NB>(); break;
                     }
                     // Read the block's DMA'd bytes back before publishing them:
                     // an LDS-DMA write is ordered only for the ISSUING wave's
@@ -1834,7 +1734,7 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
     // branch), and the inlet term added at column 0 (0 off the inlet tile)
     unsigned nv1 = kOOB, nv2 = kOOB;
     double lb_se = 0.0;
-    // narrow steady-edge blocks (BURG_SE_OPT): the column-0 source plus the
+    // narrow steady-edge blocks: the column-0 source plus the
     // inlet term, added once per block (the diagonal selects it at column 0)
     double src0_se = 0.0;
     // a column's {hx, src}; sweeps take src from their per-trajectory tables,
@@ -1906,17 +1806,6 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
         in.src = 0.0;
         if constexpr (SWEEP) in.src = b.sr[u];  // (no trajectory switch in the block)
         in.xs = lds_ld(b.wb + u * kWave);
-        in.cs = cc_ld(b.cb + u);
-        in.gw = v4u{0u, 0u, 0u, 0u};
-        in.gs = lds_ld(b.ib + u);
-        return in;
-    };
-    // the same without the previous state (the kept block: keep_of)
-    auto fetch_b_nx = [&](const Bases &b, int u) -> In {
-        In in;
-        in.nt = false;
-        in.src = 0.0;
-        in.xs = v4u{0u, 0u, 0u, 0u};
         in.cs = cc_ld(b.cb + u);
         in.gw = v4u{0u, 0u, 0u, 0u};
         in.gs = lds_ld(b.ib + u);
@@ -2019,7 +1908,7 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
         const bool at0 = SE ? u == se_uw : EDGE & (c == 0);
         // (a lane reaches column W-1 one diagonal before column 0: with U < W
         // the compare of diagonal u + 1's at0 serves as this one's atE)
-        const bool atE = SE ? ((BURG_SE_OPT && U < W) ? u + 1 == se_uw : u == se_ue)
+        const bool atE = SE ? (U < W ? u + 1 == se_uw : u == se_ue)
                             : EDGE & (c == W - 1);
         const bool need_w = has_west & at0 & valid & rowok;
         const bool need_s = has_south & (STEADY || s < KW);  // wave-uniform (lane 0 consumes)
@@ -2036,8 +1925,7 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
             const double srcc = SWEEP ? in.src : co.y;
             // (narrow steady edge: srcc + 0.0 is srcc exactly -- the source
             // term is positive -- so both forms give the same bits)
-            const double sl = (!WIDE && STEADY) ? (BURG_SE_OPT ? (at0 ? src0_se : srcc)
-                                                              : srcc + (at0 ? lb_se : 0.0))
+            const double sl = (!WIDE && STEADY) ? (at0 ? src0_se : srcc)
                                                 : (col0_tile && at0) ? srcc + lbu : srcc;
             p.hx = hx;
             const double hu = 0.5 * pu;
@@ -2210,16 +2098,16 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
     // was checked ready by block_missing.  Sweeps read one ahead, after the
     // diagonal: a lane's trajectory switch (in diagonal s) decides which
     // state and source table diagonal s + 1 reads.
-    // the kept block's outputs (keep_of: VGPRs, one block per W)
-    constexpr int KN = keep_of<W>() ? keep_n_of<W>() : 1;  // kept diagonals of the block
-    v4u kr[KN];
+    // (This empty loop is what is left of the removed kept-block experiment,
+    // it zeroed that block's register array.  Taking
+    // it out is no no-op for the compiler -- the block boundary it puts here
+    // changes the register allocation of all eight kernels, e.g. W = 256
+    // 184 -> 177 spilled SGPRs, W = 128 214 -> 236 -- so it goes with a change
+    // that measures every width, not with one that promises identical code:
+    // profiles/r07/ab/keep_remnants/README.md.)
 #pragma unroll
-    for (int u = 0; u < KN; ++u) kr[u] = v4u{0u, 0u, 0u, 0u};
-    auto run_block = [&](auto tag, const int sb, auto keep_tag) {
-        // KEEP: the kept block -- previous states from kr once the first W
-        // diagonals are past (before that the loader read them), outputs to kr
-        constexpr bool KEEP = decltype(keep_tag)::value;
-        const bool reg_ok = KEEP && sb >= W;
+    for (int u = 0; u < 1; ++u) {}
+    auto run_block = [&](auto tag, const int sb) {
         if constexpr (SWEEP && decltype(tag)::value < 3) {
             In a0 = fetch(tag, sb);
 #pragma unroll
@@ -2260,34 +2148,12 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
                 se_eoff = (east_glob & oute) ? eb + (unsigned)((a.qbase + qe) & (kR - 1)) * (kWave * G) : kOOB;
             }
             const Bases b = bases_of(sb);
-            if constexpr (KEEP) {
-                // the first W diagonals: the kept block's previous states came
-                // through the loader's window (once per launch)
-                if (!reg_ok) {
-#pragma unroll
-                    for (int u = 0; u < KN; ++u) kr[u] = lds_ld(b.wb + u * kWave);
-                }
-            }
-            // (KEEP: the previous state is kr[u], not loaded into In)
-            auto fb = [&](int u) -> In {
-                if constexpr (KEEP) {
-                    if (u < KN) {
-                        In in = fetch_b_nx(b, u);
-                        in.xs = kr[u < KN ? u : 0];
-                        return in;
-                    }
-                }
-                return fetch_b(b, u);
-            };
-            In a0 = fb(0), a1 = fb(1);
+            In a0 = fetch_b(b, 0), a1 = fetch_b(b, 1);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 In nx;
-                if (u + 2 < U) nx = fb(u + 2);
-                const v4u o = diagonal(tag, sb + u, u, a0);
-                if constexpr (KEEP) {
-                    if (u < KN) kr[u < KN ? u : 0] = o;
-                }
+                if (u + 2 < U) nx = fetch_b(b, u + 2);
+                diagonal(tag, sb + u, u, a0);
                 a0 = a1;
                 if (u + 2 < U) a1 = nx;
             }
@@ -2409,25 +2275,15 @@ __global__ __launch_bounds__(threads_of<W>()) __attribute__((amdgpu_waves_per_eu
             if ((W == 16 || W > kWave) && steady) {
                 // (narrow tiles only: the wide kernel measured 0.6 % slower
                 // with the two builds, profiles/r03/ab/steady_edge_east.txt)
-                if (!WIDE && east_glob) run_block(SteadyEdgeG(), sb, std::false_type());
-                else run_block(SteadyEdge(), sb, std::false_type());
+                if (!WIDE && east_glob) run_block(SteadyEdgeG(), sb);
+                else run_block(SteadyEdge(), sb);
             } else {
-                run_block(Edge(), sb, std::false_type());
+                run_block(Edge(), sb);
             }
         } else if (steady) {
-            if constexpr (keep_of<W>()) {
-                if (sm_ == kKeepS) run_block(Steady(), sb, std::true_type());
-                else run_block(Steady(), sb, std::false_type());
-            } else {
-                run_block(Steady(), sb, std::false_type());
-            }
+            run_block(Steady(), sb);
         } else {
-            if constexpr (keep_of<W>()) {
-                if (sm_ == kKeepS) run_block(Interior(), sb, std::true_type());
-                else run_block(Interior(), sb, std::false_type());
-            } else {
-                run_block(Interior(), sb, std::false_type());
-            }
+            run_block(Interior(), sb);
         }
         // a steady block advances the ring pointer without wrapping (it may
         // end exactly at the ring's end: the next store goes to entry 0)
@@ -2561,10 +2417,13 @@ bool set_lds_limit(const void *fn, size_t bytes)
     return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
-// workgroups per CU of the wide-tile engine: one, or two for W = 64, 128 in a
-// -DBURG_TWO_PER_CU=1 build (their LDS image fits twice); BURG_PIPE_WG_PER_CU
-// overrides (tuning knob)
-int pipe_per_cu_opt(int W)
+// workgroups per CU of the wide-tile engine: one; BURG_PIPE_WG_PER_CU=2
+// overrides (tuning knob).  The override stays because pipe_dyn_lds and the
+// occupancy query size a launch coherently for either value: with the default
+// 16-diagonal window no wide image fits a CU twice (all are above 80 KB), so 2
+// changes nothing there, and it takes effect for W = 32, 64 in a build with a
+// smaller BURG_KWIN.
+int pipe_per_cu_opt()
 {
     static int v = -1;
     if (v < 0) {
@@ -2574,7 +2433,7 @@ int pipe_per_cu_opt(int W)
             if (x >= 1 && x <= 2) v = x;
         }
     }
-    return v ? v : (BURG_TWO_PER_CU && (W == 64 || W == 128)) ? 2 : 1;
+    return v ? v : 1;
 }
 
 }  // namespace
@@ -2629,7 +2488,7 @@ int pipe_max_resident_blocks(int W, bool sweep)
         return -3;
     const void *fn = pipe_fn(W, sweep);
     if (!fn) return -1;
-    const size_t dyn = pipe_dyn_lds(W, sweep, pipe_per_cu_opt(W));
+    const size_t dyn = pipe_dyn_lds(W, sweep, pipe_per_cu_opt());
     if (dyn > 160 * 1024 || !set_lds_limit(fn, dyn)) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, pipe_threads(W), dyn) !=
         hipSuccess)
@@ -2653,7 +2512,7 @@ int launch_pipe(const PipeArgs &a, int W, hipStream_t st)
     if (a.pair && (W != 16 || a.ret_k != 0)) return -1;
     const void *fn = a.pair ? pipe_pair_fn(sweep) : pipe_fn(W, sweep);
     if (!fn) return -1;
-    const size_t dyn = pipe_dyn_lds(W, sweep, pipe_per_cu_opt(W), a.pair != 0);
+    const size_t dyn = pipe_dyn_lds(W, sweep, pipe_per_cu_opt(), a.pair != 0);
     if (dyn > 160 * 1024 || !set_lds_limit(fn, dyn)) return -1;
     // the census counter starts at zero in every launch
     if (hipMemsetAsync(a.census, 0, sizeof(unsigned), st) != hipSuccess) return -3;

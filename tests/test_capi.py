@@ -37,3 +37,29 @@ def test_abi_version_and_errors_without_gpu():
 def test_built_for_gfx950():
     so = open(os.path.join(ROOT, "finitedifference_amd", "libburgers_hip.so"), "rb").read()
     assert b"gfx950" in so
+
+
+# the default build's burg_build_flags(): csrc/Makefile's HIPFLAGS (ARCH =
+# gfx950) with "| knobs: none" appended (its FLAGSTR)
+DEFAULT_FLAGS = ("-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall "
+                 "-Wno-unused-result -Wno-bitwise-instead-of-logical | knobs: none")
+
+
+def test_flags_are_default_on_literal_strings():
+    from finitedifference_amd import _lib
+    mk = open(os.path.join(ROOT, "finitedifference_amd", "csrc", "Makefile")).read()
+    hipflags = re.search(r"^HIPFLAGS \?= (.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950")
+    assert DEFAULT_FLAGS == hipflags.strip() + " | knobs: none"
+    assert _lib.flags_are_default(DEFAULT_FLAGS)
+    base = DEFAULT_FLAGS[:-len(" | knobs: none")]
+    # a variant names its knobs (make VARIANT=cp2 KNOBS="-DBURG_COMM_PRIO=2")
+    assert not _lib.flags_are_default(base + " | knobs: -DBURG_COMM_PRIO=2")
+    # a knob passed through HIPFLAGS leaves KNOBS empty: still no default build
+    assert not _lib.flags_are_default(base + " -DBURG_STORE_WAVE=0 | knobs: none")
+    assert not _lib.flags_are_default("-O3 -DBURG_DMA_READBACK=1 --offload-arch=gfx950 | knobs: none")
+    # other flags after the knobs field, an empty string, a knob-less variant marker
+    assert not _lib.flags_are_default(DEFAULT_FLAGS + " -g")
+    assert not _lib.flags_are_default("")
+    assert not _lib.flags_are_default(base + " | knobs: -DNDEBUG")
+    # a non-BURG define in HIPFLAGS is not a knob
+    assert _lib.flags_are_default(base + " -DNDEBUG | knobs: none")
